@@ -13,8 +13,13 @@ on the data path; after sampling one RCCL all-gather of each rank's 40-byte best
 selects the global best layout (north_star). Weak scaling: --chains chains per GPU.
 
 Also reported: a VALU roofline for the step kernel (canonical algorithmic
-flops F(N,C,R) per chain-step / measured kernel time vs the 157.3 TFLOP/s FP32 vector peak) and
-the oracle's restatement of the reference chain timed on this host's cores (cpu_baseline).
+flops F(N,C,R) per chain-step / measured kernel time vs the 157.3 TFLOP/s FP32 vector peak),
+computed from the timed steps and the committed PMC record.
+
+A plain run sets up, warms up, times the steps and prints the result line. --full adds the legs
+that take runs of their own: the oracle's restatement of the reference chain timed on this
+host's cores (cpu_baseline) and the end-to-end KernelWrapperSeeded call (e2e); without it both
+fields are null. --dump-outputs DIR writes what the timed path computed (dump_outputs).
 """
 from __future__ import annotations
 
@@ -183,6 +188,34 @@ def pmc_record(n: int, n_chains_per_launch: int, step_kernel: str, srchash: str 
     return d, f"current (library {srchash[:12]})"
 
 
+DUMP_POINTS_BYTES = 32 << 20  # cap of points.npy; costs.npy is at most half of it
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(sess, out_dir: Path, rank: int, world: int) -> None:
+    """Writes what a caller of the timed path receives after its last step (Session.download():
+    every chain's final points and costs) as float32 .npy files under out_dir. Outputs larger
+    than the cap are cut to a fixed, seeded sample of chains (the same rows of points and costs;
+    sample_chains.npy names them as local chain indices). Inputs depend only on the arguments
+    (synthetic room, --seed, Philox subsequence = global chain id), so two builds run with the
+    same arguments can be compared file for file."""
+    import numpy as np
+    pts, costs = sess.download()
+    chains, n = pts.shape[0], pts.shape[1]
+    keep = min(chains, max(1, DUMP_POINTS_BYTES // (n * 6 * 4)))
+    if keep < chains:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(chains, keep, replace=False))
+    else:
+        rows = np.arange(chains)
+    all_costs = costs.nbytes <= DUMP_POINTS_BYTES // 2
+    out_dir.mkdir(parents=True, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(out_dir / f"points{tag}.npy", np.ascontiguousarray(pts[rows], dtype=np.float32))
+    np.save(out_dir / f"costs{tag}.npy",
+            np.ascontiguousarray(costs if all_costs else costs[rows], dtype=np.float32))
+    np.save(out_dir / f"sample_chains{tag}.npy", rows.astype(np.float64))
+
+
 CONFIG_NAMES = {(64, 65536): "config 3: ", (256, 32768): "config 5: ", (8, 1024): "config 2: "}
 
 
@@ -196,10 +229,18 @@ def main() -> int:
     ap.add_argument("--objects", type=int, default=64)
     ap.add_argument("--chains", type=int, default=65536, help="chains per GPU")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU baseline and "
+                         "the end-to-end KernelWrapperSeeded call (one rank only)")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="after the timed steps, write every chain's final points and costs "
+                         "(a fixed sample of chains when large) as DIR/<name>.npy")
     ap.add_argument("--cpu-budget", type=float, default=30.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--e2e-iters", type=int, default=4000,
-                    help="MH steps of the end-to-end KernelWrapperSeeded leg (0: skip)")
+                    help="with --full: MH steps of the end-to-end KernelWrapperSeeded leg "
+                         "(0: skip)")
     ap.add_argument("--collective", action="store_true",
                     help="run the process group and the best-cost all-gather even at world size "
                          "1 (the RCCL leg on device tensors with one GPU; launched without "
@@ -279,6 +320,8 @@ def main() -> int:
     # Final state, summary and the RCCL best-cost all-gather (outside the timed region).
     sess.finalize(handle)
     torch.cuda.synchronize()
+    if args.dump_outputs is not None:
+        dump_outputs(sess, args.dump_outputs, rank, world)
     s = sess.summary()
     rec = torch.tensor(summary_record(s.sum_total, s.best_total, s.best_chain, s.n_chains,
                                       s.accepted), dtype=torch.float64,
@@ -325,10 +368,10 @@ def main() -> int:
     out = None
     if rank == 0:
         e2e = None
-        if world == 1 and args.e2e_iters > 0:
+        if args.full and world == 1 and args.e2e_iters > 0:
             e2e = e2e_wrapper(mh, room, args.chains, args.e2e_iters, args.seed)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             orc = graft.load_oracle()
             cpu = cpu_baseline(room, orc, args.seed, args.cpu_budget)
         pmc, pmc_status = pmc_record(n, args.chains, step_kernel, library_srchash(mh))

@@ -367,6 +367,33 @@ def test_config4_two_rank_bench_equals_one_session(mh, hiplib, tmp_path):
     assert dist_rec["distinct_gpus"] == 1  # (two ranks share this box's one GPU)
 
 
+def test_plain_bench_dumps_the_sessions_outputs(mh, hiplib, tmp_path):
+    """A plain bench.py run (no --full): the CPU-baseline and end-to-end legs are left out, --steps
+    timed steps are reported with their ms_per_step, and --dump-outputs writes every chain's final
+    points and costs, bit for bit those of one Session run for the same number of MH steps."""
+    n, per, iters, steps, warmup, seed = 16, 1024, 100, 3, 1, 42
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--objects", str(n), "--chains",
+           str(per), "--iters", str(iters), "--steps", str(steps), "--warmup", str(warmup),
+           "--seed", str(seed), "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=150)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["cpu_baseline"] is None and rec["e2e"] is None
+    assert rec["steps"] == steps and rec["config"]["mh_steps_total"] == (steps + warmup) * iters
+    assert rec["value"] == pytest.approx(per * iters / (rec["ms_per_step"] * 1e-3), rel=1e-9)
+    with mh.Session(mh.synthetic_room(n), per, seed=seed) as s:
+        s.run((steps + warmup) * iters)
+        s.finalize()
+        pts, costs = s.download()
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == [
+        "costs.npy", "points.npy", "sample_chains.npy"]
+    got_pts = np.load(tmp_path / "out" / "points.npy")
+    got_costs = np.load(tmp_path / "out" / "costs.npy")
+    assert got_pts.dtype == np.float32 and got_costs.dtype == np.float32
+    assert np.array_equal(got_pts.view(np.uint32), pts.view(np.uint32))
+    assert np.array_equal(got_costs.view(np.uint32), costs.view(np.uint32))
+
+
 def test_kernelwrapper_mh_devices_sharding(mh, hiplib, monkeypatch):
     """$MH_DEVICES=0,0 (with $MH_DEVICES_ALLOW_DUPLICATES=1: a repeated id is otherwise an error):
     KernelWrapperSeeded shards the call over two host threads and streams (device 0 twice); the

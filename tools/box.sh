@@ -45,12 +45,12 @@ for STEP in "$@"; do
       tail -2 "$OUT/smoke.txt" ;;
     bench)
       if [ -z "$VAL" ]; then
-        timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+        timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
             || { tail -5 "$OUT/bench.err"; exit 1; }
         line "$OUT/bench.json" default
       else
         set -- ${VAL//,/ }
-        timeout -k 10 300 python bench.py --objects $1 --chains $2 --iters $3 --steps $4 --warmup 1 \
+        timeout -k 10 300 python bench.py --full --objects $1 --chains $2 --iters $3 --steps $4 --warmup 1 \
             --no-cpu-baseline > "$OUT/$NAME.json" 2> "$OUT/$NAME.err" || { tail -5 "$OUT/$NAME.err"; exit 1; }
         line "$OUT/$NAME.json" "N=$1"
       fi ;;

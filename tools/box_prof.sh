@@ -6,7 +6,7 @@ set -o pipefail
 TAG=${1:-prof}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-timeout -k 10 240 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err \
+timeout -k 10 240 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err \
     || { tail -5 $OUT/bench_default.err; exit 1; }
 tail -1 $OUT/bench_default.json | cut -c1-600
 bash tools/profile_box.sh $TAG/n64 --steps 3 --warmup 1 --iters 1000 --no-cpu-baseline || exit 1

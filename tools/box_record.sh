@@ -22,11 +22,11 @@ one() {
   python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d['roofline']; print('N=%s value=%.4g ms/launch=%.3f frac=%.4f pmc=%s valu/step=%s' % (sys.argv[2], d['value'], d['kernel_ms_per_launch'], r['frac'], r.get('pmc_status'), r.get('executed_valu_wave_insts_per_chain_step')))" $OUT/bench_n$N.json $N
 }
 one 64 "mh_kernel<64, 1, 1>" 65536 "--steps 3 --warmup 1 --iters 1000 --no-cpu-baseline --e2e-iters 0" \
-    "--steps 20 --warmup 5" || exit 1
+    "--full --steps 20 --warmup 5" || exit 1
 one 256 "mh_delta_kernel" 32768 \
     "--objects 256 --chains 32768 --steps 3 --warmup 1 --iters 1000 --no-cpu-baseline --e2e-iters 0" \
-    "--objects 256 --chains 32768 --iters 1000 --steps 8 --warmup 2 --no-cpu-baseline" || exit 1
+    "--full --objects 256 --chains 32768 --iters 1000 --steps 8 --warmup 2 --no-cpu-baseline" || exit 1
 one 8 "mh_spec_kernel" 1024 \
     "--objects 8 --chains 1024 --steps 3 --warmup 1 --iters 1000 --no-cpu-baseline --e2e-iters 0" \
-    "--objects 8 --chains 1024 --iters 2000 --steps 4 --warmup 1 --no-cpu-baseline" || exit 1
+    "--full --objects 8 --chains 1024 --iters 2000 --steps 4 --warmup 1 --no-cpu-baseline" || exit 1
 echo "box_record.sh $TAG: done"
