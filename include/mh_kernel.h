@@ -281,6 +281,48 @@ MH_API int mh_session_occupancy(const mh_session* s, int* chains_per_cu);
 
 MH_API void mh_session_destroy(mh_session* s);
 
+/* ---- suggestions: the k best mutually different layouts, selected on the device ---------- */
+
+/* The selection rule (DESIGN.md "Suggestions"). Candidates are the finalised outputs, exactly as
+ * mh_session_download returns them (with parallel tempering only the rung-0 outputs, index
+ * i % n_temps == 0); one whose totalCosts is NaN is never selected. They are ordered by
+ * totalCosts descending (a float comparison: -0 and +0 tie; ties go to the lower global chain
+ * id). d2(a, b) = max over objects i of fl(fl(dx * dx) + fl(dy * dy)), dx = fl(a.x_i - b.x_i),
+ * dy = fl(a.y_i - b.y_i), in fp32 on the float points; two layouts are the same suggestion
+ * exactly when d2 < fl(min_dist * min_dist). Walking the order, a candidate is picked when it is
+ * not the same suggestion as any earlier pick, until k are picked or none is left. */
+typedef struct mh_suggest_options {
+    int32_t k;            /* 1 .. 256 suggestions asked for */
+    float   min_dist;     /* finite, >= 0, metres; 0 = plain top-k */
+    int32_t reserved[6];  /* must be zero */
+} mh_suggest_options;     /* 32 bytes */
+
+/* After mh_session_finalize. Returns m (0..k) or -1. out_* hold m entries in pick order
+ * (out_chain_ids global ids, out_points m x nObjs points); any may be NULL. Synchronous; leaves
+ * the session's outputs untouched, so it can run, finalize and suggest again. */
+MH_API int mh_session_suggest(mh_session* s, const mh_suggest_options* o,
+                              int64_t* out_chain_ids, point* out_points, resultCosts* out_costs);
+
+/* KernelWrapperEx, but returns only the m suggestions: result[m] over one point block of
+ * m x nObjs points, freed by KernelFreeResult. *n_out = m; out_chain_ids ([k], may be NULL) gets
+ * the global chain ids. The selection is made over all of $MH_DEVICES' shards at once, so it does
+ * not depend on the sharding. m == 0 (every total NaN) returns NULL with an error text. opts may
+ * be NULL as in KernelWrapperEx. */
+MH_API result* KernelWrapperSuggest(relationshipStruct* rss, relationshipAngleStruct* rsa,
+                                    positionAndRotation* cfg, rectangle* clearances,
+                                    rectangle* offlimits, vertex* vertices,
+                                    vertex* surfaceRectangle, Surface* srf, gpuConfig* gpuCfg,
+                                    const mh_options* opts, const mh_suggest_options* sopts,
+                                    int32_t* n_out, int64_t* out_chain_ids);
+
+/* The same kernels on caller-supplied outputs (uploaded to the current device): n_chains layouts
+ * of n_objs points, their costs, `group` = tempering K (1 = every row is a candidate). Returns m
+ * or -1; out_ids ([k]) gets the picked row indices. For tests: ties, NaN, signed zeros,
+ * thresholds. */
+MH_API int mh_debug_suggest(const point* pts, const resultCosts* costs, int64_t n_chains,
+                            int n_objs, int group, const mh_suggest_options* o,
+                            int64_t* out_ids);
+
 /* ---- diagnostics -------------------------------------------------------------------------- */
 
 /* The first n Philox words, uniforms (curand_uniform stand-in) and normals (curand_normal
@@ -350,5 +392,8 @@ MH_STATIC_ASSERT(offsetof(result, costs) == 8, "result.costs");
 MH_STATIC_ASSERT(sizeof(mh_summary) == 40, "mh_summary");
 MH_STATIC_ASSERT(sizeof(mh_options) == 48, "mh_options");
 MH_STATIC_ASSERT(offsetof(mh_options, beta_min) == 24, "mh_options.beta_min");
+MH_STATIC_ASSERT(sizeof(mh_suggest_options) == 32, "mh_suggest_options");
+MH_STATIC_ASSERT(offsetof(mh_suggest_options, min_dist) == 4, "mh_suggest_options.min_dist");
+MH_STATIC_ASSERT(offsetof(mh_suggest_options, reserved) == 8, "mh_suggest_options.reserved");
 
 #endif /* MH_KERNEL_H_ */

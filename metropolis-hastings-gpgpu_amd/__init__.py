@@ -9,5 +9,6 @@ importlib) rather than a plain import.
 from .abi import (COST_FIELDS, EXPORTS, LIB_PATH, MHError, Room, Session, STRUCT_LAYOUT,  # noqa: F401
                   debug_collectives, debug_math, device_cus, debug_rng, evaluate_costs, kernel_wrapper,
                   last_error, load_library, MH_PROBE_COUNT, probe_width, release_cache,
-                  wrapper_step_kernel)
+                  wrapper_step_kernel, debug_suggest, kernel_wrapper_suggest, mh_suggest_options,
+                  suggest_options, suggest_reference, SUGGEST_MAX_K)
 from .rooms import clone_cfg, main_fixture, synthetic_room  # noqa: F401

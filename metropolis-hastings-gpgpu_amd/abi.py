@@ -90,6 +90,13 @@ class mh_options(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class mh_suggest_options(C.Structure):
+    _fields_ = [("k", C.c_int32), ("min_dist", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+SUGGEST_MAX_K = 256
+
+
 def options(seed: int, track: int = 0, rng: int = 0, temps: int = 1, swap_interval: int = 1,
             beta_min: float = 2.0) -> "mh_options":
     return mh_options(seed, track, rng, temps, swap_interval, beta_min)
@@ -114,6 +121,7 @@ STRUCT_LAYOUT = {  # (size, {field: offset}) as static_assert-ed in include/mh_k
     mh_summary: (40, {}),
     mh_options: (48, {"track_best": 8, "rng": 12, "n_temps": 16, "swap_interval": 20,
                       "beta_min": 24}),
+    mh_suggest_options: (32, {"k": 0, "min_dist": 4, "reserved": 8}),
 }
 
 COST_FIELDS = ["totalCosts", "PairWiseCosts", "VisualBalanceCosts", "FocalPointCosts",
@@ -126,7 +134,8 @@ EXPORTS = ["KernelWrapper", "KernelWrapperSeeded", "KernelWrapperEx", "KernelFre
            "mh_session_download", "mh_session_current_costs", "mh_session_summary",
            "mh_session_geometry", "mh_session_occupancy",
            "mh_session_destroy", "mh_debug_rng", "mh_debug_rng_ex", "mh_debug_collectives",
-           "mh_debug_math", "mh_debug_wrapper_step"]
+           "mh_debug_math", "mh_debug_wrapper_step",
+           "mh_session_suggest", "KernelWrapperSuggest", "mh_debug_suggest"]
 
 P = C.POINTER
 
@@ -221,6 +230,17 @@ def load_library(path: os.PathLike | str | None = None) -> C.CDLL:
     if hasattr(lib, "mh_debug_math"):  # (A/B variants of earlier revisions lack it)
         lib.mh_debug_math.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
         lib.mh_debug_math.restype = C.c_int
+    if hasattr(lib, "mh_session_suggest"):  # (A/B variants of earlier revisions lack them)
+        lib.mh_session_suggest.argtypes = [C.c_void_p, P(mh_suggest_options), P(C.c_int64),
+                                           P(point), P(resultCosts)]
+        lib.mh_session_suggest.restype = C.c_int
+        lib.KernelWrapperSuggest.argtypes = room_args + [P(gpuConfig), P(mh_options),
+                                                         P(mh_suggest_options), P(C.c_int32),
+                                                         P(C.c_int64)]
+        lib.KernelWrapperSuggest.restype = P(result)
+        lib.mh_debug_suggest.argtypes = [P(point), P(resultCosts), C.c_int64, C.c_int, C.c_int,
+                                         P(mh_suggest_options), P(C.c_int64)]
+        lib.mh_debug_suggest.restype = C.c_int
     if path is None:
         _lib = lib
     return lib
@@ -309,6 +329,91 @@ def kernel_wrapper(room: Room, chains: int, iterations: int, seed: int | None = 
     finally:
         lib.KernelFreeResult(res)
     return p, costs
+
+
+def suggest_options(k: int, min_dist: float) -> "mh_suggest_options":
+    return mh_suggest_options(k, min_dist)
+
+
+def kernel_wrapper_suggest(room: Room, chains: int, iterations: int, seed: int, k: int,
+                           min_dist: float, block_x: int = 64, track: int = MH_TRACK_OFF,
+                           rng: int = MH_RNG_PHILOX, temps: int = 1, swap_interval: int = 1,
+                           beta_min: float = 2.0):
+    """KernelWrapperSuggest: runs the chains as kernel_wrapper does and returns only the m <= k
+    suggestions, (global chain ids int64 [m], points float32 [m, N, 6], costs float32 [m, 8]) in
+    pick order."""
+    lib = load_library()
+    g = gpuConfig(chains, 0, block_x, 0, 0, iterations)
+    opts = options(seed, track, rng, temps, swap_interval, beta_min)
+    so = suggest_options(k, min_dist)
+    m = C.c_int32(-1)
+    ids = (C.c_int64 * max(k, 1))()
+    res = lib.KernelWrapperSuggest(*room.args(), C.byref(g), C.byref(opts), C.byref(so),
+                                   C.byref(m), ids)
+    if not res:
+        raise MHError(last_error(lib))
+    try:
+        n, cnt = room.n, m.value
+        pts = (point * (cnt * n)).from_address(C.cast(res[0].points, C.c_void_p).value)
+        p = np.frombuffer(bytes(memoryview(pts)), dtype=np.float32).reshape(cnt, n, 6).copy()
+        rs = (result * cnt).from_address(C.cast(res, C.c_void_p).value)
+        costs = np.array([[getattr(rs[i].costs, f) for f in COST_FIELDS] for i in range(cnt)],
+                         dtype=np.float32)
+        base = C.cast(res[0].points, C.c_void_p).value  # one block, result[i] at i * N
+        assert C.cast(rs[cnt - 1].points, C.c_void_p).value == base + (cnt - 1) * n * C.sizeof(point)
+    finally:
+        lib.KernelFreeResult(res)
+    return np.array(ids[:cnt], dtype=np.int64), p, costs
+
+
+def debug_suggest(pts, costs, k: int, min_dist: float, group: int = 1) -> np.ndarray:
+    """mh_debug_suggest: the suggestion kernels on caller-supplied outputs, points float32
+    [chains, N, 6] and costs float32 [chains, 8]; returns the picked row indices int64 [m]."""
+    lib = load_library()
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    costs = np.ascontiguousarray(costs, dtype=np.float32)
+    chains, n = pts.shape[0], pts.shape[1]
+    if pts.shape != (chains, n, 6) or costs.shape != (chains, 8):
+        raise ValueError("points must be [chains, N, 6] and costs [chains, 8]")
+    so = suggest_options(k, min_dist)
+    ids = (C.c_int64 * max(k, 1))()
+    m = lib.mh_debug_suggest(pts.ctypes.data_as(P(point)), costs.ctypes.data_as(P(resultCosts)),
+                             chains, n, group, C.byref(so), ids)
+    if m < 0:
+        raise MHError(last_error(lib))
+    return np.array(ids[:m], dtype=np.int64)
+
+
+def suggest_reference(points, costs, k: int, min_dist: float, ids=None, group: int = 1):
+    """The selection rule of include/mh_kernel.h ("suggestions") restated in numpy, every
+    operation in np.float32: candidates are the rows i with i % group == 0 whose total is not NaN,
+    ordered by total descending (ties: lower id); a candidate is picked when its d2 (the maximum
+    over objects of dx*dx + dy*dy) to every earlier pick is not below min_dist*min_dist. `ids`
+    are the rows' global chain ids (default: the row indices). Returns what Session.suggest
+    returns: (ids int64 [m], points [m, N, 6], costs [m, 8]) in pick order."""
+    pts = np.asarray(points, dtype=np.float32)
+    cs = np.asarray(costs, dtype=np.float32)
+    tot = cs[:, 0]
+    gid = np.arange(len(tot), dtype=np.int64) if ids is None else np.asarray(ids, dtype=np.int64)
+    cand = [i for i in range(len(tot)) if i % group == 0 and not np.isnan(tot[i])]
+    # (a float comparison: -0.0 and +0.0 compare equal, +-inf are ordinary values)
+    cand.sort(key=lambda i: (-float(tot[i]), int(gid[i])))
+    with np.errstate(over="ignore", invalid="ignore"):
+        md2 = np.float32(min_dist) * np.float32(min_dist)
+        x, y = pts[:, :, 0], pts[:, :, 1]
+        picks = []
+        for i in cand:
+            if len(picks) == k:
+                break
+            if picks:
+                dx = x[i][None, :] - x[picks]
+                dy = y[i][None, :] - y[picks]
+                d2 = (dx * dx + dy * dy).max(axis=1)  # each product and the sum rounded to fp32
+                if bool((d2 < md2).any()):
+                    continue
+            picks.append(i)
+    picks = np.array(picks, dtype=np.int64)
+    return gid[picks], pts[picks], cs[picks]
 
 
 STEP_KINDS = {0: "full", 1: "incremental", 2: "full-few", 3: "speculative"}
@@ -458,6 +563,21 @@ class Session:
         if self.lib.mh_session_summary(self.h, C.byref(s)) != 0:
             raise MHError(last_error(self.lib))
         return s
+
+    def suggest(self, k: int, min_dist: float):
+        """mh_session_suggest after finalize(): the m <= k best mutually different layouts, picked
+        on the device; (global chain ids int64 [m], points float32 [m, N, 6], costs float32
+        [m, 8]) in pick order."""
+        n = self.room.n
+        so = suggest_options(k, min_dist)
+        ids = (C.c_int64 * max(k, 1))()
+        pts = (point * (max(k, 1) * n))()
+        cs = (resultCosts * max(k, 1))()
+        m = self.lib.mh_session_suggest(self.h, C.byref(so), ids, pts, cs)
+        if m < 0:
+            raise MHError(last_error(self.lib))
+        p = np.frombuffer(bytes(pts), dtype=np.float32).reshape(max(k, 1), n, 6)[:m].copy()
+        return np.array(ids[:m], dtype=np.int64), p, costs_to_array(cs)[:m]
 
     def geometry(self):
         """(lanes per chain, chains per workgroup) of the step kernel."""

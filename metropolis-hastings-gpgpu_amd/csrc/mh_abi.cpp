@@ -429,6 +429,15 @@ struct mh_session {
     point* d_pts = nullptr;
     resultCosts* d_costs = nullptr;
     mh_summary* d_summary = nullptr;
+    // Suggestions (suggest_rounds): the candidates' alive bytes, one key per round, the
+    // reference layout's x, y, the packed x, y copy of d_pts, and a small pinned block
+    // the rounds' read-backs and the reference layout's upload go through.
+    unsigned char* d_alive = nullptr;
+    unsigned long long* d_skey = nullptr;
+    float2* d_sref = nullptr;
+    float2* d_sxy = nullptr;
+    unsigned char* h_sug = nullptr;
+    size_t cap_hsug = 0;
     // Download staging: two pinned chunks the library allocates (hipHostMalloc) and owns. A
     // download DMAs chunk k into one while the host copies chunk k - 1 out of the other into the
     // caller's buffer, which is never page-locked (hipHostRegister) -- see copy_out.
@@ -439,7 +448,7 @@ struct mh_session {
     // its buffers across calls and grows one only when a call needs more.
     size_t cap_obj = 0, cap_clr = 0, cap_rel = 0, cap_rele = 0, cap_cfg0 = 0, cap_st = 0, cap_best = 0,
            cap_xw = 0, cap_ladder = 0, cap_perm = 0, cap_meta = 0, cap_pts = 0, cap_costs = 0,
-           cap_summary = 0;
+           cap_summary = 0, cap_alive = 0, cap_skey = 0, cap_sref = 0, cap_sxy = 0;
     // The geometry's inputs (choose_geometry runs only when they change)
     bool geo_valid = false;
     int geo_n = -1, geo_c = -1, geo_r = -1;
@@ -506,6 +515,11 @@ void free_session(mh_session* s) {
     (void)hipFree(s->d_pts);
     (void)hipFree(s->d_costs);
     (void)hipFree(s->d_summary);
+    (void)hipFree(s->d_alive);
+    (void)hipFree(s->d_skey);
+    (void)hipFree(s->d_sref);
+    (void)hipFree(s->d_sxy);
+    if (s->h_sug) (void)hipHostFree(s->h_sug);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     for (hipEvent_t e : s->stage_ev)
         if (e) (void)hipEventDestroy(e);
@@ -779,6 +793,188 @@ bool session_download(mh_session* s, point* pts, resultCosts* costs) {
     return true;
 }
 
+// ---- suggestions: the k best mutually different layouts (DESIGN.md "Suggestions") ------------
+
+constexpr int kSuggestMaxK = 256;
+
+bool check_suggest_options(const mh_suggest_options* o, const char* name) {
+    if (!o) { set_error(std::string(name) + " is NULL"); return false; }
+    char buf[160];
+    if (o->k < 1 || o->k > kSuggestMaxK) {
+        snprintf(buf, sizeof buf, "mh_suggest_options.k must be in [1, %d] (got %d)", kSuggestMaxK, o->k);
+        set_error(buf);
+        return false;
+    }
+    if (!(o->min_dist >= 0.0f) || !(o->min_dist <= FLT_MAX)) {
+        set_error("mh_suggest_options.min_dist must be finite and >= 0");
+        return false;
+    }
+    for (int k = 0; k < 6; ++k)
+        if (o->reserved[k] != 0) {
+            set_error("mh_suggest_options.reserved must be zero");
+            return false;
+        }
+    return true;
+}
+
+// The pinned block of a session's rounds: the round's key, then the winner's costs and points,
+// then the reference layout (x, y) on its way up.
+struct SuggestPin {
+    unsigned long long* key;
+    resultCosts* costs;
+    point* pts;
+    float2* ref;
+};
+
+SuggestPin suggest_pin(const mh_session* s) {
+    const size_t n = (size_t)s->room.rm.n;
+    SuggestPin p;
+    p.key = static_cast<unsigned long long*>(static_cast<void*>(s->h_sug));
+    p.costs = static_cast<resultCosts*>(static_cast<void*>(s->h_sug + 32));
+    p.pts = static_cast<point*>(static_cast<void*>(s->h_sug + 64));
+    p.ref = static_cast<float2*>(static_cast<void*>(s->h_sug + 64 + sizeof(point) * n));
+    return p;
+}
+
+bool suggest_prepare(mh_session* s, int k) {
+    MH_TRY_HIP(hipSetDevice(s->device));
+    if (s->n_chains >= (1LL << 32)) {
+        set_error("suggest: a session must hold fewer than 2^32 chains");
+        return false;
+    }
+    if (s->n_chains <= 0) return true;
+    const size_t n = (size_t)s->room.rm.n, nc = (size_t)s->n_chains;
+    if (!ensure(&s->d_alive, s->cap_alive, nc)) return false;
+    if (!ensure(&s->d_skey, s->cap_skey, (size_t)kSuggestMaxK)) return false;
+    if (!ensure(&s->d_sref, s->cap_sref, n)) return false;
+    if (!ensure(&s->d_sxy, s->cap_sxy, n * nc)) return false;
+    const size_t pin = 64 + (sizeof(point) + sizeof(float2)) * n;
+    if (!s->h_sug || s->cap_hsug < pin) {
+        if (s->h_sug) (void)hipHostFree(s->h_sug);
+        s->h_sug = nullptr;
+        s->cap_hsug = 0;
+        MH_TRY_HIP(hipHostMalloc((void**)&s->h_sug, pin, hipHostMallocDefault));
+        s->cap_hsug = pin;
+    }
+    if (!order_after_last(s, s->stream)) return false;
+    MH_TRY_HIP(mh::launch_suggest_reset(s->d_costs, s->d_pts, s->n_chains, (int)n, s->n_temps,
+                                        s->d_alive, s->d_skey, k, s->d_sxy,
+                                        s->stream));
+    return true;
+}
+
+// Drives the rounds over the shards of one call (a single session is the one-shard case). Every
+// round is global: each shard's kernel names its best survivor, the host takes the best of those
+// by (total, global chain id), fetches that one layout and sends its x, y back to every shard
+// as the next round's reference. (A local top-k per shard merged on the host would not be exact:
+// a chain another shard's pick removes can survive locally and shadow one the rule keeps.)
+// Returns the number of picks, or -1. Leaves d_pts and d_costs untouched.
+int suggest_rounds_run(const std::vector<mh_session*>& shards, const mh_suggest_options& o,
+                       int64_t* out_ids, point* out_pts, resultCosts* out_costs) {
+    const float md2 = o.min_dist * o.min_dist;
+    size_t n = 0;
+    for (mh_session* s : shards) {
+        if (!suggest_prepare(s, o.k)) return -1;
+        n = (size_t)s->room.rm.n;
+    }
+    auto fail = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return false;
+        set_error(std::string("suggest: ") + what + ": " + hipGetErrorString(e));
+        return true;
+    };
+    std::vector<int64_t> kill(shards.size(), -1);
+    int m = 0;
+    for (; m < o.k; ++m) {
+        for (size_t i = 0; i < shards.size(); ++i) {
+            mh_session* s = shards[i];
+            if (s->n_chains <= 0) continue;
+            if (fail(hipSetDevice(s->device), "hipSetDevice")) return -1;
+            if (fail(mh::launch_suggest_round(s->d_sxy, s->d_costs,
+                                              s->n_chains, (int)n, m > 0 ? s->d_sref : nullptr,
+                                              md2, kill[i], s->d_alive, s->d_skey + m, s->stream),
+                     "round"))
+                return -1;
+            kill[i] = -1;
+            if (fail(hipMemcpyAsync(suggest_pin(s).key, s->d_skey + m, sizeof(unsigned long long),
+                                    hipMemcpyDeviceToHost, s->stream), "key read-back"))
+                return -1;
+        }
+        int win = -1;
+        uint32_t win_order = 0;
+        int64_t win_local = 0, win_id = 0;
+        for (size_t i = 0; i < shards.size(); ++i) {
+            mh_session* s = shards[i];
+            if (s->n_chains <= 0) continue;
+            if (fail(hipSetDevice(s->device), "hipSetDevice")) return -1;
+            if (fail(hipStreamSynchronize(s->stream), "round")) return -1;
+            const unsigned long long key = *suggest_pin(s).key;
+            if (key == 0) continue;  // nobody is left on this shard
+            const uint32_t order = (uint32_t)(key >> 32);
+            const int64_t local = (int64_t)(0xFFFFFFFFu - (uint32_t)key);
+            const int64_t id = s->chain_offset + local;
+            if (win < 0 || order > win_order || (order == win_order && id < win_id)) {
+                win = (int)i;
+                win_order = order;
+                win_local = local;
+                win_id = id;
+            }
+        }
+        if (win < 0) break;  // no candidate is left anywhere
+        mh_session* w = shards[(size_t)win];
+        if (win_local >= w->n_chains) {
+            set_error("suggest: internal: a round key names a chain outside its shard");
+            return -1;
+        }
+        const SuggestPin wp = suggest_pin(w);
+        if (fail(hipSetDevice(w->device), "hipSetDevice")) return -1;
+        if (fail(hipMemcpyAsync(wp.pts, w->d_pts + n * (size_t)win_local, sizeof(point) * n,
+                                hipMemcpyDeviceToHost, w->stream), "winner read-back") ||
+            fail(hipMemcpyAsync(wp.costs, w->d_costs + win_local, sizeof(resultCosts),
+                                hipMemcpyDeviceToHost, w->stream), "winner read-back") ||
+            fail(hipStreamSynchronize(w->stream), "winner read-back"))
+            return -1;
+        if (out_ids) out_ids[m] = win_id;
+        if (out_pts) memcpy(out_pts + n * (size_t)m, wp.pts, sizeof(point) * n);
+        if (out_costs) out_costs[m] = *wp.costs;
+        kill[(size_t)win] = win_local;
+        if (m + 1 == o.k) continue;  // (no further round reads a reference)
+        for (mh_session* s : shards) {
+            if (s->n_chains <= 0) continue;
+            const SuggestPin sp = suggest_pin(s);
+            // (the shard's previous upload from this block completed before its last
+            // synchronisation above)
+            for (size_t i = 0; i < n; ++i) sp.ref[i] = make_float2(wp.pts[i].x, wp.pts[i].y);
+            if (fail(hipSetDevice(s->device), "hipSetDevice")) return -1;
+            if (fail(hipMemcpyAsync(s->d_sref, sp.ref, sizeof(float2) * n, hipMemcpyHostToDevice,
+                                    s->stream), "reference upload"))
+                return -1;
+        }
+    }
+    return m;
+}
+
+// The rounds, then the sessions' `done` events: on success and on failure alike every shard's
+// stream is drained and its event recorded after whatever the rounds queued, so that later work
+// on any stream is ordered after it (a failed call leaves no kernel or copy in flight).
+int suggest_rounds(const std::vector<mh_session*>& shards, const mh_suggest_options& o,
+                   int64_t* out_ids, point* out_pts, resultCosts* out_costs) {
+    int m = suggest_rounds_run(shards, o, out_ids, out_pts, out_costs);
+    const bool failed = m < 0;
+    const std::string err = g_last_error;
+    for (mh_session* s : shards) {
+        if (!s->stream || hipSetDevice(s->device) != hipSuccess) continue;
+        const hipError_t e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess && m >= 0) {
+            set_error(std::string("suggest: ") + hipGetErrorString(e));
+            m = -1;
+        } else if (s->done && !record_done(s, s->stream) && m >= 0) {
+            m = -1;
+        }
+    }
+    if (failed) set_error(err);  // (the rounds' own error, not the drain's)
+    return m;
+}
+
 // ---- KernelWrapper's session cache -----------------------------------------------------------
 // A KernelWrapper call runs one session per device: a stream and an event, a dozen device
 // buffers, the geometry (occupancy queries), the room upload, then the launches and the copy
@@ -967,29 +1163,85 @@ struct Shard {
     int lanes = -1, kind = -1;  // the step kernel its session ran (mh_session_geometry's codes)
     bool ok = false;
     std::string err;
+    mh_session* kept = nullptr;  // KernelWrapperSuggest: the finalised session, for the rounds
 };
+
+// What every KernelWrapper* call sets up before its shards run: the validated room, the calling
+// thread's device and the shards over $MH_DEVICES (whole tempering groups; K = 1 without
+// tempering).
+struct WrapperPlan {
+    Room room;
+    int current = 0;
+    int64_t chains = 0;
+    int iterations = 0;
+    size_t n = 0;
+    std::vector<Shard> shards;
+};
+
+bool wrapper_plan(relationshipStruct* rss, relationshipAngleStruct* rsa, positionAndRotation* cfg,
+                  rectangle* clearances, rectangle* offlimits, vertex* vertices,
+                  vertex* surfaceRectangle, Surface* srf, gpuConfig* gpuCfg,
+                  const mh_options& opts, WrapperPlan& p) {
+    if (!gpuCfg) { set_error("gpuCfg is NULL"); return false; }
+    if (gpuCfg->gridxDim < 1) { set_error("gpuConfig.gridxDim must be >= 1"); return false; }
+    if (gpuCfg->iterations < 0) { set_error("gpuConfig.iterations must be >= 0"); return false; }
+    if (!build_room(rss, rsa, cfg, clearances, offlimits, vertices, surfaceRectangle, srf, p.room))
+        return false;
+    if (hipGetDevice(&p.current) != hipSuccess) {
+        set_error("no HIP device available");
+        return false;
+    }
+    p.chains = gpuCfg->gridxDim;
+    p.iterations = gpuCfg->iterations;
+    p.n = (size_t)srf->nObjs;
+    std::vector<int> devs;
+    if (!devices_from_env(p.current, devs)) return false;
+    if ((int64_t)devs.size() > p.chains) devs.resize((size_t)p.chains);
+    const int64_t K = opts.n_temps > 1 ? opts.n_temps : 1;
+    if (p.chains % K != 0) {
+        set_error("parallel tempering: gridxDim must be a multiple of n_temps");
+        return false;
+    }
+    const int64_t groups = p.chains / K;
+    if ((int64_t)devs.size() > groups) devs.resize((size_t)groups);
+    p.shards.assign(devs.size(), Shard{});
+    for (size_t k = 0; k < devs.size(); ++k) {
+        p.shards[k].device = devs[k];
+        p.shards[k].begin = K * (groups * (int64_t)k / (int64_t)devs.size());
+        p.shards[k].count = K * (groups * (int64_t)(k + 1) / (int64_t)devs.size()) - p.shards[k].begin;
+    }
+    return true;
+}
+
+// Runs `work` on every shard (one host thread per shard when there are several), notes the first
+// shard's step kernel and returns to the calling thread's device.
+template <class Work>
+void run_shards(WrapperPlan& p, Work&& work) {
+    if (p.shards.size() == 1) {
+        work(p.shards[0]);
+    } else {
+        std::vector<std::thread> th;
+        for (auto& sh : p.shards) th.emplace_back(work, std::ref(sh));
+        for (auto& t : th) t.join();
+    }
+    g_wrapper_lanes = p.shards[0].lanes;
+    g_wrapper_kind = p.shards[0].kind;
+    (void)hipSetDevice(p.current);
+}
 
 result* wrapper_impl(relationshipStruct* rss, relationshipAngleStruct* rsa, positionAndRotation* cfg,
                      rectangle* clearances, rectangle* offlimits, vertex* vertices,
                      vertex* surfaceRectangle, Surface* srf, gpuConfig* gpuCfg,
                      const mh_options& opts) {
-    if (!gpuCfg) { set_error("gpuCfg is NULL"); return nullptr; }
-    if (gpuCfg->gridxDim < 1) { set_error("gpuConfig.gridxDim must be >= 1"); return nullptr; }
-    if (gpuCfg->iterations < 0) { set_error("gpuConfig.iterations must be >= 0"); return nullptr; }
-    Room room;
-    if (!build_room(rss, rsa, cfg, clearances, offlimits, vertices, surfaceRectangle, srf, room))
+    WrapperPlan plan;
+    if (!wrapper_plan(rss, rsa, cfg, clearances, offlimits, vertices, surfaceRectangle, srf, gpuCfg,
+                      opts, plan))
         return nullptr;
-    int current = 0;
-    if (hipGetDevice(&current) != hipSuccess) {
-        set_error("no HIP device available");
-        return nullptr;
-    }
-    const int64_t chains = gpuCfg->gridxDim;
-    const int iterations = gpuCfg->iterations;
-    const size_t n = (size_t)srf->nObjs;
-    std::vector<int> devs;
-    if (!devices_from_env(current, devs)) return nullptr;
-    if ((int64_t)devs.size() > chains) devs.resize((size_t)chains);
+    const Room& room = plan.room;
+    const int64_t chains = plan.chains;
+    const int iterations = plan.iterations;
+    const size_t n = plan.n;
+    std::vector<Shard>& shards = plan.shards;
 
     point* pts = (point*)malloc(sizeof(point) * n * (size_t)chains);
     result* res = (result*)malloc(sizeof(result) * (size_t)chains);
@@ -999,22 +1251,6 @@ result* wrapper_impl(relationshipStruct* rss, relationshipAngleStruct* rsa, posi
         free(res);
         set_error("host allocation failed");
         return nullptr;
-    }
-    // Shard whole tempering groups (K = 1 without tempering).
-    const int64_t K = opts.n_temps > 1 ? opts.n_temps : 1;
-    if (chains % K != 0) {
-        free(pts);
-        free(res);
-        set_error("parallel tempering: gridxDim must be a multiple of n_temps");
-        return nullptr;
-    }
-    const int64_t groups = chains / K;
-    if ((int64_t)devs.size() > groups) devs.resize((size_t)groups);
-    std::vector<Shard> shards(devs.size());
-    for (size_t k = 0; k < devs.size(); ++k) {
-        shards[k].device = devs[k];
-        shards[k].begin = K * (groups * (int64_t)k / (int64_t)devs.size());
-        shards[k].count = K * (groups * (int64_t)(k + 1) / (int64_t)devs.size()) - shards[k].begin;
     }
     // The result block's pages are mapped on a host thread of their own while the shards'
     // kernels run; a shard downloads only after that (the mapping writes the pages).
@@ -1039,18 +1275,7 @@ result* wrapper_impl(relationshipStruct* rss, relationshipAngleStruct* rsa, posi
             session_give_back(s);
         }
     };
-    if (shards.size() == 1) {
-        work(shards[0]);
-        g_wrapper_lanes = shards[0].lanes;
-        g_wrapper_kind = shards[0].kind;
-    } else {
-        std::vector<std::thread> th;
-        for (auto& sh : shards) th.emplace_back(work, std::ref(sh));
-        for (auto& t : th) t.join();
-        g_wrapper_lanes = shards[0].lanes;
-        g_wrapper_kind = shards[0].kind;
-    }
-    (void)hipSetDevice(current);
+    run_shards(plan, work);
     for (auto& sh : shards) {
         if (!sh.ok) {
             free(pts);
@@ -1062,6 +1287,77 @@ result* wrapper_impl(relationshipStruct* rss, relationshipAngleStruct* rsa, posi
     for (int64_t i = 0; i < chains; ++i) {
         res[i].points = pts + n * (size_t)i;
         res[i].costs = costs[(size_t)i];
+    }
+    g_last_error.clear();
+    return res;
+}
+
+// KernelWrapperSuggest: wrapper_impl's shards run and finalise their sessions and keep them; the
+// calling thread then drives the rounds over all of them and downloads only the picks.
+result* suggest_impl(relationshipStruct* rss, relationshipAngleStruct* rsa, positionAndRotation* cfg,
+                     rectangle* clearances, rectangle* offlimits, vertex* vertices,
+                     vertex* surfaceRectangle, Surface* srf, gpuConfig* gpuCfg,
+                     const mh_options& opts, const mh_suggest_options& so, int32_t* n_out,
+                     int64_t* out_chain_ids) {
+    WrapperPlan plan;
+    if (!wrapper_plan(rss, rsa, cfg, clearances, offlimits, vertices, surfaceRectangle, srf, gpuCfg,
+                      opts, plan))
+        return nullptr;
+    const size_t n = plan.n;
+    const int iterations = plan.iterations;
+    auto work = [&](Shard& sh) {
+        mh_session* s = session_borrow(plan.room, sh.device, sh.count, sh.begin, opts);
+        if (!s) {
+            sh.err = g_last_error;
+            return;
+        }
+        (void)mh_session_geometry(s, &sh.lanes, nullptr, &sh.kind);
+        sh.ok = session_run(s, iterations, s->stream) && session_finalize(s, s->stream);
+        if (!sh.ok) sh.err = g_last_error;
+        sh.kept = s;
+    };
+    run_shards(plan, work);
+    std::vector<mh_session*> sessions;
+    std::string err;
+    for (auto& sh : plan.shards) {
+        if (!sh.ok && err.empty()) err = "device " + std::to_string(sh.device) + ": " + sh.err;
+        if (sh.kept) sessions.push_back(sh.kept);
+    }
+    std::vector<int64_t> ids((size_t)so.k);
+    std::vector<resultCosts> costs((size_t)so.k);
+    std::vector<point> picked(n * (size_t)so.k);
+    int m = -1;
+    if (err.empty()) {
+        m = suggest_rounds(sessions, so, ids.data(), picked.data(), costs.data());
+        if (m < 0) err = g_last_error;
+    }
+    for (mh_session* s : sessions) {
+        if (m < 0) free_session(s);  // (a failed session is not reused)
+        else session_give_back(s);
+    }
+    (void)hipSetDevice(plan.current);
+    if (m < 0) {
+        set_error(err);
+        return nullptr;
+    }
+    *n_out = m;
+    if (m == 0) {
+        set_error("no suggestion: every candidate's totalCosts is NaN");
+        return nullptr;
+    }
+    point* pts = (point*)malloc(sizeof(point) * n * (size_t)m);
+    result* res = (result*)malloc(sizeof(result) * (size_t)m);
+    if (!pts || !res) {
+        free(pts);
+        free(res);
+        set_error("host allocation failed");
+        return nullptr;
+    }
+    memcpy(pts, picked.data(), sizeof(point) * n * (size_t)m);
+    for (int i = 0; i < m; ++i) {
+        res[i].points = pts + n * (size_t)i;
+        res[i].costs = costs[(size_t)i];
+        if (out_chain_ids) out_chain_ids[i] = ids[(size_t)i];
     }
     g_last_error.clear();
     return res;
@@ -1097,6 +1393,62 @@ MH_API result* KernelWrapperEx(relationshipStruct* rss, relationshipAngleStruct*
     if (!check_options(opts)) return nullptr;
     return wrapper_impl(rss, rsa, cfg, clearances, offlimits, vertices, surfaceRectangle, srf,
                         gpuCfg, *opts);
+}
+
+MH_API result* KernelWrapperSuggest(relationshipStruct* rss, relationshipAngleStruct* rsa,
+                                    positionAndRotation* cfg, rectangle* clearances,
+                                    rectangle* offlimits, vertex* vertices,
+                                    vertex* surfaceRectangle, Surface* srf, gpuConfig* gpuCfg,
+                                    const mh_options* opts, const mh_suggest_options* sopts,
+                                    int32_t* n_out, int64_t* out_chain_ids) {
+    // (all of this before the first HIP call)
+    if (!n_out) { set_error("n_out is NULL"); return nullptr; }
+    *n_out = 0;
+    if (!check_suggest_options(sopts, "sopts")) return nullptr;
+    if (opts && !check_options(opts)) return nullptr;
+    return suggest_impl(rss, rsa, cfg, clearances, offlimits, vertices, surfaceRectangle, srf,
+                        gpuCfg, opts ? *opts : default_options(seed_from_env()), *sopts, n_out,
+                        out_chain_ids);
+}
+
+MH_API int mh_session_suggest(mh_session* s, const mh_suggest_options* o, int64_t* out_chain_ids,
+                              point* out_points, resultCosts* out_costs) {
+    if (!s) { set_error("NULL session"); return -1; }
+    if (!check_suggest_options(o, "o")) return -1;
+    return suggest_rounds(std::vector<mh_session*>{s}, *o, out_chain_ids, out_points, out_costs);
+}
+
+MH_API int mh_debug_suggest(const point* pts, const resultCosts* costs, int64_t n_chains,
+                            int n_objs, int group, const mh_suggest_options* o, int64_t* out_ids) {
+    if (!check_suggest_options(o, "o")) return -1;
+    if (!pts || !costs || !out_ids || n_chains < 0 || n_objs < 1 || group < 1) {
+        set_error("bad arguments");
+        return -1;
+    }
+    if (n_chains == 0) return 0;
+    // A bare session around the caller's outputs: no room, no chains to step; only what
+    // suggest_rounds reads.
+    mh_session* s = new mh_session();
+    const size_t n = (size_t)n_objs, nc = (size_t)n_chains;
+    s->room.rm.n = n_objs;
+    s->n_chains = n_chains;
+    s->n_temps = group;
+    auto setup = [&]() {
+        MH_TRY_HIP(hipGetDevice(&s->device));
+        MH_TRY_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        MH_TRY_HIP(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
+        if (!ensure(&s->d_pts, s->cap_pts, n * nc)) return false;
+        if (!ensure(&s->d_costs, s->cap_costs, nc)) return false;
+        MH_TRY_HIP(hipMemcpyAsync(s->d_pts, pts, sizeof(point) * n * nc, hipMemcpyHostToDevice, s->stream));
+        MH_TRY_HIP(hipMemcpyAsync(s->d_costs, costs, sizeof(resultCosts) * nc, hipMemcpyHostToDevice, s->stream));
+        return record_done(s, s->stream);
+    };
+    int m = -1;
+    if (setup()) m = suggest_rounds(std::vector<mh_session*>{s}, *o, out_ids, nullptr, nullptr);
+    const std::string err = g_last_error;
+    free_session(s);
+    if (m < 0) set_error(err);
+    return m;
 }
 
 MH_API void KernelFreeResult(result* res) {

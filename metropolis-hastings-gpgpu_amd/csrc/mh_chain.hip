@@ -1956,6 +1956,114 @@ __global__ void __launch_bounds__(1024) mh_summary_kernel(const resultCosts* cos
     }
 }
 
+// ---- diverse top-K suggestions (DESIGN.md "Suggestions") ----------------------------------
+// k rounds of "take the best survivor, then remove it and everything within min_dist of it",
+// over the finalised outputs. The host (mh_abi.cpp suggest_rounds) drives the rounds: a round is
+// global over every shard of a call, so each shard reports its best survivor and the host names
+// the winner, whose x, y come back as the next round's reference layout.
+
+// Order-preserving map of a non-NaN float onto unsigned: a > b as floats <=> map(a) > map(b),
+// with -0 folded into +0 first so that the two tie. Never 0 (-inf maps to 0x007FFFFF).
+__device__ __forceinline__ unsigned int suggest_order(float t) {
+    const unsigned int b = __float_as_uint(t == 0.0f ? 0.0f : t);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// max that keeps a NaN from either side (fmaxf would drop it): the rule's plain maximum.
+__device__ __forceinline__ float suggest_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+template <int OFF>
+__device__ __forceinline__ unsigned long long suggest_key_max(unsigned long long k) {
+    const unsigned int lo = (unsigned int)bfly<OFF>((int)(unsigned int)k);
+    const unsigned int hi = (unsigned int)bfly<OFF>((int)(unsigned int)(k >> 32));
+    const unsigned long long p = ((unsigned long long)hi << 32) | lo;
+    return p > k ? p : k;
+}
+
+__global__ void __launch_bounds__(256) mh_suggest_reset_kernel(
+    const resultCosts* costs, const point* pts, int64_t n_chains, int n, int group,
+    unsigned char* alive, unsigned long long* keys, int n_keys, float2* xy) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = tid; i < n_chains; i += stride) {
+        const float t = costs[i].totalCosts;
+        alive[i] = (i % group == 0 && t == t) ? 1 : 0;
+    }
+    for (int64_t i = tid; i < n_keys; i += stride) keys[i] = 0ull;
+    const int64_t total = n_chains * n;
+    for (int64_t i = tid; i < total; i += stride) xy[i] = make_float2(pts[i].x, pts[i].y);
+}
+
+// One round. L lanes per candidate; lane r of a group takes the objects r, r + L, ... A
+// workgroup strides over passes of 256 / L candidates and keeps its best survivor's key, so a
+// round issues at most one atomic per workgroup of a grid that fills the GPU once (one atomic
+// per 256 / L candidates measured 188 us per round at 65,536 candidates, all of it the atomics
+// queueing on one address; profiles/suggest_n64.txt). A wavefront none of whose candidates is
+// alive leaves a pass after reading the alive bytes; the butterflies of the others run in
+// wave-uniform control flow. `pos` is the reset pass's packed x, y copy of the outputs (reading
+// the outputs themselves, at their 24-byte stride, measured 6% slower per call at config 3's
+// shape: profiles/suggest_n64.txt).
+template <int L>
+__global__ void __launch_bounds__(256) mh_suggest_round_kernel(
+    const float2* pos, const resultCosts* costs, int64_t n_chains, int n, const float2* ref, float md2,
+    int64_t kill, unsigned char* alive, unsigned long long* key) {
+    constexpr int G = 256 / L;
+    __shared__ unsigned long long s_key[4];
+    const int r = (int)threadIdx.x % L;
+    const int64_t passes = (n_chains + G - 1) / G;
+    unsigned long long k = 0ull;
+    for (int64_t p = blockIdx.x; p < passes; p += gridDim.x) {  // (workgroup-uniform trip count)
+        const int64_t c = p * G + (int)threadIdx.x / L;
+        bool live = c < n_chains && alive[c] != 0;
+        if (__ballot(live) == 0) continue;  // nobody in this wavefront is left
+        if (live && c == kill) {  // the previous round's winner (also at min_dist = 0)
+            live = false;
+            if (r == 0) alive[c] = 0;
+        }
+        if (ref) {
+            float m = -INFINITY;
+            if (live) {
+                const float2* row = pos + c * n;
+                for (int i = r; i < n; i += L) {
+                    const float2 q = ref[i];
+                    const float dx = row[i].x - q.x, dy = row[i].y - q.y;
+                    m = suggest_max(m, dx * dx + dy * dy);
+                }
+            }
+            m = suggest_max(m, bfly<1>(m));
+            m = suggest_max(m, bfly<2>(m));
+            m = suggest_max(m, bfly<4>(m));
+            if constexpr (L >= 16) m = suggest_max(m, bfly<8>(m));
+            if constexpr (L >= 32) m = suggest_max(m, bfly<16>(m));
+            if constexpr (L >= 64) m = suggest_max(m, bfly<32>(m));
+            if (live && m < md2) {  // the same suggestion as the reference layout
+                live = false;
+                if (r == 0) alive[c] = 0;
+            }
+        }
+        if (live) {
+            const unsigned long long kc =
+                ((unsigned long long)suggest_order(costs[c].totalCosts) << 32) |
+                (0xFFFFFFFFu - (unsigned int)c);
+            k = kc > k ? kc : k;
+        }
+    }
+    // (uniform within a group already: only the levels across groups)
+    if constexpr (L <= 8) k = suggest_key_max<8>(k);
+    if constexpr (L <= 16) k = suggest_key_max<16>(k);
+    if constexpr (L <= 32) k = suggest_key_max<32>(k);
+    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = k;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        k = s_key[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) k = s_key[w] > k ? s_key[w] : k;
+        // (the key only grows within a round: a workgroup that cannot raise it need not try)
+        if (k != 0ull && k > __hip_atomic_load(key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMax(key, k);
+    }
+}
+
 // ---- RNG diagnostic: the exact draws a chain sees --------------------------------------
 
 __global__ void mh_rng_kernel(uint64_t seed, uint64_t subsequence, int n, unsigned int* u32,
@@ -2233,6 +2341,47 @@ hipError_t launch_summary(const resultCosts* costs, const ChainMeta* meta, int64
                           int64_t chain_offset, mh_summary* out, hipStream_t s) {
     hipLaunchKernelGGL(mh_summary_kernel, dim3(1), dim3(1024), 0, s, costs, meta, n, chain_offset, out);
     return hipGetLastError();
+}
+
+hipError_t launch_suggest_reset(const resultCosts* costs, const point* pts, int64_t n_chains, int n,
+                                int group, unsigned char* alive, unsigned long long* keys,
+                                int n_keys, float2* xy, hipStream_t s) {
+    int64_t work = n_chains * n;
+    if (work < n_keys) work = n_keys;
+    if (work <= 0) return hipSuccess;
+    const int64_t blocks = (work + 255) / 256 < 16384 ? (work + 255) / 256 : 16384;
+    hipLaunchKernelGGL(mh_suggest_reset_kernel, dim3((unsigned)blocks), dim3(256), 0, s, costs, pts,
+                       n_chains, n, group > 1 ? group : 1, alive, keys, n_keys, xy);
+    return hipGetLastError();
+}
+
+// Workgroups of a round: eight per CU of a 256-CU part, each striding over the candidates.
+constexpr int64_t kSuggestBlocks = 2048;
+
+template <int L>
+static hipError_t launch_suggest_round_l(const float2* xy, const resultCosts* costs, int64_t n_chains, int n,
+                                         const float2* ref, float md2, int64_t kill,
+                                         unsigned char* alive, unsigned long long* key,
+                                         hipStream_t s) {
+    constexpr int G = 256 / L;
+    const int64_t passes = (n_chains + G - 1) / G;
+    const dim3 grid((unsigned)(passes < kSuggestBlocks ? passes : kSuggestBlocks)), block(256);
+    hipLaunchKernelGGL(mh_suggest_round_kernel<L>, grid, block, 0, s, xy, costs, n_chains, n, ref,
+                       md2, kill, alive, key);
+    return hipGetLastError();
+}
+
+// Lanes per candidate: the smallest of 8, 16, 32, 64 that covers n (more objects: several per lane).
+hipError_t launch_suggest_round(const float2* xy, const resultCosts* costs,
+                                int64_t n_chains, int n, const float2* ref, float md2,
+                                int64_t kill, unsigned char* alive, unsigned long long* key,
+                                hipStream_t s) {
+    if (n_chains <= 0) return hipSuccess;
+    if (n_chains >= (1LL << 32) || n < 1) return hipErrorInvalidValue;  // (the key's index word)
+    if (n <= 8) return launch_suggest_round_l<8>(xy, costs, n_chains, n, ref, md2, kill, alive, key, s);
+    if (n <= 16) return launch_suggest_round_l<16>(xy, costs, n_chains, n, ref, md2, kill, alive, key, s);
+    if (n <= 32) return launch_suggest_round_l<32>(xy, costs, n_chains, n, ref, md2, kill, alive, key, s);
+    return launch_suggest_round_l<64>(xy, costs, n_chains, n, ref, md2, kill, alive, key, s);
 }
 
 #if MH_CHECK

@@ -61,6 +61,19 @@ int delta_max_waves(int n);  // chains per workgroup the incremental kernel admi
 int step_blocks_per_cu(int L, int npl, int waves_per_wg, size_t lds_bytes, bool few);
 hipError_t launch_summary(const resultCosts* costs, const ChainMeta* meta, int64_t n,
                           int64_t chain_offset, mh_summary* out, hipStream_t s);
+// Suggestions (mh_chain.hip "diverse top-K suggestions"). The reset pass marks the candidates
+// (alive[i] = 1 unless i % group != 0 or costs[i].totalCosts is NaN), clears n_keys round keys
+// and packs the points' x, y into xy [n_chains][n]. A round reads the positions from xy; removes
+// the candidate `kill` (-1: none) and, when ref ([n] x, y) is given, every live candidate with d2
+// to it below md2; then raises *key to the best survivor's (order word of its total << 32 |
+// 0xFFFFFFFF - index); 0 = nobody is left.
+hipError_t launch_suggest_reset(const resultCosts* costs, const point* pts, int64_t n_chains, int n,
+                                int group, unsigned char* alive, unsigned long long* keys,
+                                int n_keys, float2* xy, hipStream_t s);
+hipError_t launch_suggest_round(const float2* xy, const resultCosts* costs,
+                                int64_t n_chains, int n, const float2* ref, float md2,
+                                int64_t kill, unsigned char* alive, unsigned long long* key,
+                                hipStream_t s);
 hipError_t launch_collectives(int L, const float* v, const int* iv, int* out, hipStream_t s);
 hipError_t launch_step_xw(const LaunchArgs& a, int L, int npl, int waves_per_wg, hipStream_t s);
 hipError_t launch_step_best(const LaunchArgs& a, int L, int npl, int waves_per_wg, hipStream_t s);
