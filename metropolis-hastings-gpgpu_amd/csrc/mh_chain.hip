@@ -380,7 +380,41 @@ __device__ __forceinline__ int inc_cl_update(const ChainPtrs& ch, int n, int c, 
 #define MH_EVAL_ATTR __attribute__((noinline))
 #endif
 
-template <int L, int NPL, bool WITH_OL, bool DELTA, bool FAST = false, bool PAIRS = false>
+// Makes this lane's symmetry row exact where it is carried as a marked estimate (SymRows,
+// mh_common.h): its leader's value by the reference's formula, floored at 0 (Kernel.cu:303).
+// (rx, ry, rr) is the row's reflected pose. Call with every lane of the wavefront active.
+template <int L, int NPL>
+__device__ __forceinline__ void sym_exactify(const ChainPtrs& ch, const OwnPose<NPL>& op, int gbase,
+                                             int n, float rx, float ry, float rr, float& mx,
+                                             int& arg, bool count) {
+    const bool mk = sym_marked(arg);
+    const uint64_t any = __ballot(mk);
+    if (any) {
+        const int j = sym_col(arg);
+        const double ryj = pose_ry_var<L, NPL>(op, j, gbase);
+        if (mk) {
+            MH_CK(j < n, 9, j, n);
+            const ObjP q = ch.P[j];
+            const float e = sym_val_exact(q.xf, q.yf, ryj, rx, ry, (double)rr);
+            MH_CK(fabsf(fmaxf(0.0f, e) - mx) <= sym_err(mx, rr), 33, __float_as_uint(e),
+                  __float_as_uint(mx));
+            mx = fmaxf(0.0f, e);
+            arg = e > 0.0f ? j : -1;
+        }
+#if MH_CHECK
+        if (count && __lane_id() == (unsigned)__builtin_ctzll(any)) {
+            MH_SYMC(0, 1);
+            MH_SYMC(2, __builtin_popcountll(any));
+            MH_SYMC(3, 1);
+        }
+#endif
+    }
+}
+
+// MARKS: `prev` may hold marked estimates (the plain steps' exact passes: 1; the check build's
+// verifying evaluation, which stays out of the counters: 2).
+template <int L, int NPL, bool WITH_OL, bool DELTA, bool FAST = false, bool PAIRS = false,
+          int MARKS = 0>
 __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch, const OwnPose<NPL>& op,
                            int r, int gbase,
                            float out[8], SymRows<NPL>& sym, const SymRows<NPL>& prev, int ka,
@@ -540,12 +574,12 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
     // bound is proven for (exact_mode) evaluates every pair exactly.
     if (r == 0) MH_PHASE(ch, 1, t0);
     const bool exact_mode = group_ballot<L>(wild, gbase) != 0;
-    // Steps that decide on the rejection bound leave a re-scanned row's maximum as its leader's
-    // fp32 estimate (the bound adds its allowance, esym); the leader's exact value is evaluated
-    // only if the step is not certainly rejected (below), when the row enters a commit or a sum.
-    constexpr bool DEFER_SYM = FAST;  // (one chain per wavefront, one object per lane)
-    int dlead = -1;
-    float esym = 0.0f;
+    // Steps that decide on the rejection bound (FAST: one chain per wavefront, one object per
+    // lane) carry a row whose leader is clear as a marked estimate (SymRows): the bound adds its
+    // allowance, a certain accept commits it as it is, and the leader's exact value is evaluated
+    // only when a step needs the exact sums (sym_exactify below, and at the start of the exact
+    // passes of the current configuration).
+    static_assert(!FAST || (NPL == 1 && MARKS == 0), "marked rows: one object per lane");
     if constexpr (!DELTA) {
     // Full scan: keep the two largest estimates per row and evaluate the leader exactly. When
     // the top two are closer than their error bounds the row falls back to the exact value of
@@ -668,15 +702,92 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
     const double rya = pose_ry<L, NPL>(op, ka < 0 ? 0 : ka, gbase);
     const double ryb = pose_ry<L, NPL>(op, kb < 0 ? 0 : kb, gbase);
     bool any_pend = false;
+    SymRows<NPL> pv = prev;
+    if constexpr (FAST) {
+        // Unchanged row r against the changed columns, on estimates alone. The row's cached
+        // maximum cm (allowance ec; 0 if exact) is the maximum over the unchanged columns and the
+        // floor unless a changed column held it. A changed column k with estimate v: certainly
+        // below (v + ev < cm - ec) keeps the row; certainly above (v - ev > cm + ec; >= if k held
+        // the maximum, whose other columns stay <= it) makes k the clear leader and the row a
+        // marked estimate (v, k), certainly > 0 as cm - ec >= 0; the second column is then set
+        // against that. The old leader's column not certainly at or above its old value (or
+        // following a column that rose), and estimates that overlap within their allowances,
+        // are left to the re-scan below, which is exact wherever its estimates do not separate.
+        const bool row = r < n;
+        float cm = pv.mx[0];
+        bool mk = sym_marked(pv.arg[0]);
+        int ca = sym_col(pv.arg[0]);
+        need[0] = row && (r == ka || r == kb || exact_mode);
+        pend[0] = 0u;
+        bool ovl = false;
+        if (row && !need[0]) {
+            const float rr = rrs[0];
+            float ec = mk ? sym_err(cm, rr) : 0.0f;
+            const int ca0 = ca;
+            if (ka >= 0) {
+                const float v = sym_val_fast(qa, rxs[0], rys[0], rr);
+                const float ev = sym_err(v, rr);
+                const bool held = ka == ca0;
+                if (held ? v - ev >= cm + ec : v - ev > cm + ec) {
+                    cm = v;
+                    ec = ev;
+                    ca = ka;
+                    mk = true;
+                } else if (held) {
+                    need[0] = true;
+                } else if (!(v + ev < cm - ec)) {
+                    ovl = true;
+                }
+            }
+            if (kb >= 0) {
+                const float v = sym_val_fast(qb, rxs[0], rys[0], rr);
+                const float ev = sym_err(v, rr);
+                const bool held = kb == ca0;
+                if (held && ca != ca0) {
+                    need[0] = true;  // (its old leader moved and column ka rose: re-scan)
+                } else if (held ? v - ev >= cm + ec : v - ev > cm + ec) {
+                    cm = v;
+                    ec = ev;
+                    ca = kb;
+                    mk = true;
+                } else if (held) {
+                    need[0] = true;
+                } else if (!(v + ev < cm - ec)) {
+                    ovl = true;
+                }
+            }
+        }
+#if MH_CHECK
+        if (const uint64_t ob = __ballot(ovl && !need[0]); ob && r == __builtin_ctzll(ob))
+            MH_SYMC(1, __builtin_popcountll(ob));
+#endif
+        need[0] = need[0] || ovl;
+        sym.mx[0] = cm;
+        sym.arg[0] = mk ? (ca | kSymMark) : ca;
+    } else {
+    if constexpr (MARKS != 0) {
+        // A marked row of `prev`: its leader's exact value where neither the row nor the leader's
+        // column changed (the pair is the same in both configurations); a re-scan otherwise.
+        static_assert(NPL == 1, "marked rows: one object per lane");
+        const int lc = sym_col(pv.arg[0]);
+        const bool redo = sym_marked(pv.arg[0]) && (r == ka || r == kb || lc == ka || lc == kb);
+        if (redo) {
+            pv.mx[0] = 0.0f;
+            pv.arg[0] = -1;
+        }
+        sym_exactify<L, NPL>(ch, op, gbase, n, rxs[0], rys[0], rrs[0], pv.mx[0], pv.arg[0],
+                             MARKS == 1);
+        need[0] = redo;
+    }
 #pragma unroll
     for (int m = 0; m < NPL; ++m) {
         const int i = m * L + r;
         const bool row = i < n;
-        const float cm = prev.mx[m];
-        const int ca = prev.arg[m];
+        const float cm = pv.mx[m];
+        const int ca = pv.arg[m];
         sym.mx[m] = cm;
         sym.arg[m] = ca;
-        need[m] = row && (i == ka || i == kb);
+        need[m] = row && (i == ka || i == kb || (MARKS != 0 && need[m]));
         pend[m] = 0u;
         if (row && !need[m]) {
             // A changed column's pair is pending (exact value needed) unless its estimate is
@@ -698,9 +809,10 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
         }
         any_pend |= pend[m] != 0u;
     }
+    }
     // Exact values of the pending (row, column) pairs: one evaluation site, each lane taking
-    // its lowest pending slot per pass.
-    while (__ballot(any_pend)) {
+    // its lowest pending slot per pass. (FAST leaves none pending.)
+    while (!FAST && __ballot(any_pend)) {
         if (any_pend) {
             int ms = NPL - 1;
 #pragma unroll
@@ -716,7 +828,7 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
             for (int m = 0; m < NPL; ++m) {
                 if (m == ms) {
                     pend[m] &= pend[m] - 1u;
-                    if (col == prev.arg[m] && !(e >= prev.mx[m])) {
+                    if (col == pv.arg[m] && !(e >= pv.mx[m])) {
                         need[m] = true;  // the old maximum is gone: re-scan the row
                     } else if (e > sym.mx[m]) {
                         sym.mx[m] = e;
@@ -767,8 +879,19 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
         const SymLead ld = group_sym_lead<L>(t1, t2, tj, r, gbase, rr);
         float best = 0.0f;
         int barg = -1;
-        const bool clear = !exact_mode && ld.clear;
+        // (FAST: a clear leader stays an estimate where its sign is certain -- above 0 the row is
+        // marked, at or below 0 the floor is the exact maximum; a leader whose sign is not certain
+        // is evaluated exactly at once, as an unclear one)
+        const float es = sym_err(ld.m, rr);
+        const bool clear =
+            !exact_mode && ld.clear && !(FAST && !(ld.m - es > 0.0f) && !(ld.m + es <= 0.0f));
         if (!clear) {
+#if MH_CHECK
+            if (FAST && r == b) {  // (estimates that do not separate: resolved exactly)
+                MH_SYMC(0, 1);
+                MH_SYMC(1, 1);
+            }
+#endif
             const float thr =
                 (exact_mode || ld.j < 0) ? INFINITY : 2.0f * sym_err(fabsf(ld.m) + 1.0f, rr);
             float bv = -INFINITY;
@@ -796,10 +919,10 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
         for (int m = 0; m < NPL; ++m) {
             if (m == ms) {
                 if (r == b) {
-                    if (clear && DEFER_SYM) {
-                        dlead = ld.j;
-                        esym = sym_err(ld.m, rr);
-                        sym.mx[m] = fmaxf(0.0f, ld.m);
+                    if (FAST && clear) {
+                        const bool pos = ld.m - es > 0.0f;
+                        sym.mx[m] = pos ? ld.m : 0.0f;
+                        sym.arg[m] = pos ? (ld.j | kSymMark) : -1;
                     } else if (clear) {
                         lead[m] = ld.j;
                         leadp |= 1u << m;
@@ -813,7 +936,7 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
             any_row |= rows[m] != 0;
         }
     }
-    while (__ballot(leadp != 0u)) {
+    while (!FAST && __ballot(leadp != 0u)) {
         const int ms = leadp ? __builtin_ctz(leadp) : 0;
         const int j = leadp ? sel<NPL>(lead, ms) : 0;
         const double ryj = pose_ry_var<L, NPL>(op, j, gbase);  // (every lane active)
@@ -859,6 +982,28 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
     if (r == 0) MH_PHASE(ch, 3, t0);
     if constexpr (FAST) {
         static_assert(INC_CL && L == 64, "the rejection bound needs one chain per wavefront");
+#if MH_CHECK
+        {   // every row of the proposed state against a fresh exact scan: a marked row's leader
+            // within the allowance and attaining the row's exact maximum, an unmarked row exact
+            float fresh = -INFINITY, el = 0.0f;
+            const int lj = sym_col(sym.arg[0]);
+            for (int j = 0; j < n; ++j) {
+                const double ryj = pose_ry<L, NPL>(op, j, gbase);
+                const ObjP q = ch.P[j];
+                const float e = sym_val_exact(q.xf, q.yf, ryj, rxs[0], rys[0], (double)rrs[0]);
+                fresh = fmaxf(fresh, e);
+                el = j == lj ? e : el;
+            }
+            if (r < n && sym_marked(sym.arg[0])) {
+                MH_CK(fabsf(fmaxf(0.0f, el) - sym.mx[0]) <= sym_err(sym.mx[0], rrs[0]), 33,
+                      __float_as_uint(el), __float_as_uint(sym.mx[0]));
+                MH_CK(el == fresh && el > 0.0f, 34, __float_as_uint(el), __float_as_uint(fresh));
+            } else if (r < n) {
+                MH_CK(sym.mx[0] == fmaxf(0.0f, fresh), 35, __float_as_uint(sym.mx[0]),
+                      __float_as_uint(fresh));
+            }
+        }
+#endif
         if (rm.r <= L) {  // every relationship term is held by a lane (rpw[0], rang[0])
             // this lane's object against the clearances it overlaps: kept from the current
             // configuration unless its column may have changed
@@ -897,6 +1042,8 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
                 MH_CK(f == clsum, 28, __float_as_uint(f), __float_as_uint(clsum));
             }
 #endif
+            // (every marked row's allowance, this step's and those carried from earlier steps)
+            const float esym = sym_marked(sym.arg[0]) ? sym_err(sym.mx[0], rrs[0]) : 0.0f;
             BoundTerms bt;
             bt.nx = px0;
             bt.ny = py[0];
@@ -932,31 +1079,13 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
                 stage(ch.aux)->cyc[10] += d == BOUND_ACCEPT ? 1 : 0;
             }
 #endif
-            if (d == BOUND_REJECT) {
+            if (d != BOUND_OPEN) {  // (a certain accept commits the marked rows as they are)
                 *fast = d;
                 return;
             }
-            if constexpr (DEFER_SYM) {
-                // the deferred leaders' exact values (every lane active for the rotY read)
-                if (__ballot(dlead >= 0)) {
-                    const int j = dlead >= 0 ? dlead : 0;
-                    const double ryj = pose_ry_var<L, NPL>(op, j, gbase);
-                    if (dlead >= 0) {
-                        const ObjP q = ch.P[j];
-                        const float e = sym_val_exact(q.xf, q.yf, ryj, rxs[0], rys[0],
-                                                      (double)rrs[0]);
-                        MH_CK(fabsf(fmaxf(0.0f, e) - sym.mx[0]) <= esym, 33,
-                              __float_as_uint(e), __float_as_uint(sym.mx[0]));
-                        sym.mx[0] = fmaxf(0.0f, e);
-                        sym.arg[0] = e > 0.0f ? j : -1;
-                    }
-                }
-                if (d != BOUND_OPEN) {
-                    *fast = d;
-                    return;
-                }
-            }
             // The exact sums are needed: every estimated term is made exact first.
+            sym_exactify<L, NPL>(ch, op, gbase, n, rxs[0], rys[0], rrs[0], sym.mx[0], sym.arg[0],
+                                 true);
             const bool obj = r < n && clo.dc, rel = r < rm.r && clo.dr;
             if (__ballot(obj || rel)) {
                 float c0 = cph[0];
@@ -980,6 +1109,9 @@ __device__ MH_EVAL_ATTR void eval_costs(const LaunchArgs& a, const ChainPtrs& ch
             }
             clo.dc = clo.dr = false;
             clo.eang = 0.0f;
+        } else {  // (no bound: the sums below read exact rows)
+            sym_exactify<L, NPL>(ch, op, gbase, n, rxs[0], rys[0], rrs[0], sym.mx[0], sym.arg[0],
+                                 true);
         }
     }
     // The eight ordered sums of Costs() -- VisualBalance nx and ny (float through double
@@ -1669,8 +1801,8 @@ __global__ void __launch_bounds__(512) MH_OCC mh_kernel(LaunchArgs a) {
                     float cx[8];
                     SymRows<NPL> sx;
                     ClPairs clx;
-                    eval_costs<L, NPL, false, true>(a, ch, op, r, gbase, cx, sx, sym, kk.x, kk.y,
-                                                    clx, cl);
+                    eval_costs<L, NPL, false, true, false, false, 2>(a, ch, op, r, gbase, cx, sx,
+                                                                     sym, kk.x, kk.y, clx, cl);
                     chk_star = uniform_f(cx[0]);
                     if (r == 0) atomicAdd(&g_check[5], 1u);
                     const bool acc_x =
@@ -1684,6 +1816,8 @@ __global__ void __launch_bounds__(512) MH_OCC mh_kernel(LaunchArgs a) {
                               __float_as_uint(chk_cur));
                     }
                 }
+                // (exact current costs: no row of the current state is a marked estimate)
+                MH_CK(!cur_exact || !sym_marked(sym.arg[0]), 36, sym.arg[0], r);
                 if (r == 0)
                     MH_CK(chk_cur >= cur_iv.lo && chk_cur <= cur_iv.hi, 23,
                           __float_as_uint(chk_cur), __float_as_uint(cur_iv.hi - cur_iv.lo));
@@ -1722,10 +1856,11 @@ __global__ void __launch_bounds__(512) MH_OCC mh_kernel(LaunchArgs a) {
                     restore<L, NPL>(ch, op, r, writer, kk);
                     hand_off(ch.P, ch.aux);  // the current configuration again
                     float cx[8];
-                    SymRows<NPL> sx;
                     ClPairs clx;
-                    eval_costs<L, NPL, false, true>(a, ch, op, r, gbase, cx, sx, ss, kk.x, kk.y, clx,
-                                                    cls);
+                    // (the current rows are written over by their exact values: none stays a
+                    // marked estimate beside exact current costs)
+                    eval_costs<L, NPL, false, true>(a, ch, op, r, gbase, cx, sym, ss, kk.x, kk.y,
+                                                    clx, cls);
                     if (writer) {
                         const Staged<ChainAux> ax = stage(ch.aux);
                         for (int k = 0; k < 8; ++k) ax->cur[k] = cx[k];
@@ -1807,7 +1942,9 @@ __global__ void __launch_bounds__(512) MH_OCC mh_kernel(LaunchArgs a) {
             float cx[8];
             SymRows<NPL> sx;
             ClPairs clx;
-            eval_costs<L, NPL, false, true>(a, ch, op, r, gbase, cx, sx, sym, -1, -1, clx, cl);
+            // (its rows may be marked estimates: made exact first)
+            eval_costs<L, NPL, false, true, false, false, (!TRACK && FASTK_OF(L, NPL)) ? 1 : 0>(
+                a, ch, op, r, gbase, cx, sx, sym, -1, -1, clx, cl);
             if (writer)
                 for (int k = 0; k < 8; ++k) stage(ch.aux)->cur[k] = cx[k];
             hand_off(ch.aux);
@@ -2392,6 +2529,11 @@ extern "C" __attribute__((visibility("default"))) int mh_debug_check(unsigned in
 extern "C" __attribute__((visibility("default"))) int mh_debug_decisions(unsigned long long* out) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_decide), sizeof(unsigned long long) * 4) ==
+                   hipSuccess ? 0 : -1;
+}
+extern "C" __attribute__((visibility("default"))) int mh_debug_symrows(unsigned long long* out) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_symc), sizeof(unsigned long long) * 4) ==
                    hipSuccess ? 0 : -1;
 }
 #endif

@@ -36,6 +36,11 @@ static __device__ unsigned int g_check[8];  // (per translation unit) [0] violat
 static __device__ unsigned long long g_decide[4];  // steps that evaluated the bound, certain
                                                    // rejects, certain accepts, exact passes of
                                                    // the current configuration
+static __device__ unsigned long long g_symc[4];  // bound-deciding steps' symmetry rows, per
+                                                 // wavefront pass: [0] sym_val_exact passes, [1] of
+                                                 // them resolutions of overlapping estimates,
+                                                 // [2] marked rows made exact, [3] such passes
+#define MH_SYMC(k, v) atomicAdd(&g_symc[(k)], (unsigned long long)(v))
 __device__ __forceinline__ void mh_count_decision(int d, bool evaluated) {
     if (evaluated) atomicAdd(&g_decide[0], 1ull);
     if (d == 1) atomicAdd(&g_decide[1], 1ull);
@@ -1258,11 +1263,19 @@ __device__ __forceinline__ bool certain_reject(const DevRoom& rm, int n, int c, 
 
 // Exact row maxima of the symmetry rows this lane owns (rows m * L + r), with the column that
 // attains each (-1: the 0 floor of Kernel.cu:303 is the maximum).
+// Steps that decide on the rejection bound (eval_costs FAST) may carry a row as a marked
+// estimate instead: arg = kSymMark | j, mx = the fp32 estimate of column j, a clear leader whose
+// exact value is the row's exact maximum and certainly > 0; |mx - exact| <= sym_err(mx, rr) with
+// rr the row's own reflected angle, which phase A forms each step. sym_exactify() makes such
+// rows exact before anything reads a row as the reference's value.
 template <int NPL>
 struct SymRows {
     float mx[NPL];
     int arg[NPL];
 };
+constexpr int kSymMark = 0x40000000;
+__device__ __forceinline__ bool sym_marked(int arg) { return arg >= kSymMark; }
+__device__ __forceinline__ int sym_col(int arg) { return arg < 0 ? -1 : (arg & (kSymMark - 1)); }
 
 // Non-zero Clearance pairs of a configuration, for the incremental pair update of the
 // full-evaluation step (one object per lane): this lane's column mask (bit i: clearance i

@@ -26,7 +26,10 @@ SITES = {20: "certain REJECT but Accept accepts", 21: "certain ACCEPT but Accept
          30: "a FocalPoint estimate outside kDeltaCph",
          31: "a PairWise estimate outside kPwEstU U",
          32: "a PairWiseAngle estimate outside its allowance",
-         33: "a deferred Symmetry row maximum outside its estimate's allowance",
+         33: "a marked Symmetry row's estimate outside its allowance",
+         34: "a marked Symmetry row's leader is not the row's exact maximum (or not > 0)",
+         35: "an unmarked Symmetry row differs from a fresh exact scan",
+         36: "exact current costs beside a marked Symmetry row",
          14: "the final pass's output slot outside [0, n_chains)",
          16: "the final pass's OffLimits boxes outside the chain's LDS slot"}
 
@@ -114,6 +117,17 @@ def one(kind, n, chains, steps, kernel):
     rates = (f"; of {chains * steps} steps: certain reject {dc[1] / steps_all:.4f}, certain "
              f"accept {dc[2] / steps_all:.4f}, open {(dc[0] - dc[1] - dc[2]) / steps_all:.4f}, "
              f"exact current pass {dc[3] / steps_all:.4f}") if dc[0] else ""
+    if kernel == "full" and dc[0]:
+        # the symmetry rows carried as marked estimates (one chain per wavefront): how often the
+        # exact pair value is still evaluated, beside the steps that need exact rows
+        sr = (C.c_ulonglong * 4)()
+        assert lib.mh_debug_symrows(sr) == 0
+        launches = -(-steps // 1000)  # (kStepsPerLaunch, mh_abi.cpp)
+        rates += (f"; symmetry rows: {sr[0]} exact passes, {sr[1]} overlap resolutions, {sr[2]} "
+                  f"marked rows in {sr[3]} exactifying passes, {dc[0] - dc[1] - dc[2]} open steps, "
+                  f"{dc[3]} exact current passes, {launches} launches "
+                  f"({sr[0] / steps_all:.5f} exact passes and {sr[1] / steps_all:.5f} resolutions "
+                  f"per chain-step)")
     site = SITES.get(ck[1], str(ck[1]))
     # (speculative: decisions at every evaluated node, the realised path's and the others')
     print(f"[bound] {kind} N={n} {kernel}: {chains} x {steps} steps, {ck[5]} bound decisions "
